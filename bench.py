@@ -8,9 +8,14 @@ north_star's 1e-3 dB against the reference's fp32 arithmetic (conv error 4.7e-7 
 the bf16-headed split (bf16x3, the headline of rounds 5 -- 6a), the bf16 throughput mode and the exact-f32 mode are carried as extra legs.  At N = 1 the same run is
 repeated at batch 128 and reported as `throughput_at_batch_128` (per-image cost falls with batch).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either under a launcher -- python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ... -- or
    plainly as `python bench.py --gpus N`, which starts the N ranks itself)
+
+A plain run sets up, warms up, times the K steps and prints the headline line; the extra legs below (roofline, power, hipGraph
+replay, batch 128, the other arithmetic modes, CPU baseline) run only with --full.  --dump-outputs DIR writes the sampler state
+the timed path returned after its last step (rank 0: all ranks' images, as gathered) to DIR/x_last_step.npy, float32; the
+inputs are seeded, so two builds can be compared output for output.
 
 A "step" is one Heun sampler step of the 100-step Karras schedule over one batch of 16 synthetic
 images (2 guided-denoiser calls = 2 UNet forwards + 2 hand-written UNet VJPs + 2 mat-solves, CG
@@ -19,7 +24,7 @@ K < 100 the K timed steps are spread evenly over the schedule (so the closed-for
 preserved) and each starts from x0 + sigma_i * noise.  Inputs are resident in HBM before the
 timed region.  value = images/s of the whole job = N * batch / (100 * seconds_per_step).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but the multi-GPU evidence only with --full):
   roofline     dominant kernel (bf16 3x3 implicit-GEMM conv): algorithmic FLOPs / HIP-event time,
                measured live in an extra profiled pass after the timed region
                (+ hbm_bound_classes: GroupNorm / operator / point-wise kernels in GB/s; op_bandwidth_at_64_images)
@@ -88,6 +93,23 @@ def step_indices(K, n=100, last_single=True):
     if K == 1:
         return [n // 2]
     return [int(round(j * (n - (2 if last_single else 1)) / (K - 1))) for j in range(K)]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: each tensor as outdir/<name>.npy in float32.  A tensor above 64 MB in all is cut to a fixed, seeded
+    sample of whole images (sorted indices along dim 0), so that runs with the same arguments write the same sample."""
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            per = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], max(budget // per, 1), replace=False))
+            a = a[keep]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def available_cores():
@@ -294,12 +316,17 @@ def main():
                                                                   "(no GPU work: also runs on a CPU-only host, where the ranks rendezvous over gloo)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the extra legs (roofline, power samples, hipGraph replay, batch 128, the other arithmetic modes, "
+                                                        "CPU baseline; each can still be turned off by its --no-* flag).  Without it the run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy (float32, at most 64 MB)")
     args = ap.parse_args()
     WL = WORKLOADS[args.workload]
     if args.batch is None:
         args.batch = WL["batch"]
     if args.workload != "cfg1":      # the extra legs and the CPU baseline belong to the headline workload
         args.no_large_batch = args.no_graph_leg = args.no_f32_leg = args.no_cpu_baseline = True
+    if not args.full:
+        args.no_large_batch = args.no_graph_leg = args.no_f32_leg = args.no_cpu_baseline = args.no_roofline = True
 
     # `python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): start the N ranks ourselves, one process per
     # GPU under torch.distributed.run on the loopback address, pass the arguments through and relay rank 0's JSON line.
@@ -407,18 +434,22 @@ def main():
         env.barrier()
         elapsed = env.max_over_ranks(time.perf_counter() - t0)
         assert torch.isfinite(hat).all() and hat.shape[0] == env.world_size * x.shape[0]
+        timed_run.hat = hat
         return elapsed
 
     full_run = args.steps % NS == 0 and args.steps > 0
     idx = step_indices(args.steps, NS, last_single=heun)
     parts = build_parts(B, args.streams)
     S_ = len(parts)
-    sampler = PowerSampler() if env.is_main_process and not os.environ.get("KDIP_NO_POWER") else None
+    sampler = PowerSampler() if args.full and env.is_main_process and not os.environ.get("KDIP_NO_POWER") else None
     if sampler:
         with sampler:
             elapsed = timed_run(parts, idx, full_run, args.warmup)
     else:
         elapsed = timed_run(parts, idx, full_run, args.warmup)
+    if args.dump_outputs and env.is_main_process:
+        dump_outputs(args.dump_outputs, {"x_last_step": timed_run.hat})
+    del timed_run.hat
     den, x0 = parts[0]["den"], parts[0]["x0"]             # the roofline leg profiles part 0 alone
 
     gather_ms = env.max_over_ranks(getattr(timed_run, "gather_ms", 0.0))
@@ -623,7 +654,7 @@ def main():
         torch.cuda.empty_cache()
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--dtype", args.dtype, "--batch", "128", "--streams", str(args.streams), "--steps", str(args.steps),
-                                "--warmup", "2", "--no-cpu-baseline", "--no-roofline", "--no-large-batch", "--no-f32-leg", "--no-graph-leg"], capture_output=True, text=True, timeout=1500)
+                                "--warmup", "2", "--full", "--no-cpu-baseline", "--no-roofline", "--no-large-batch", "--no-f32-leg", "--no-graph-leg"], capture_output=True, text=True, timeout=1500)
             big = json.loads(r.stdout.strip().splitlines()[-1])
             out["throughput_at_batch_128"] = {"value": big["value"], "unit": "images/s", "per_gpu_batch": 128,
                                               "streams_per_gpu": big["config"]["streams_per_gpu"], "ms_per_step": big["ms_per_step"],
@@ -640,7 +671,7 @@ def main():
 
         def sub_leg(dtype, steps, flags):
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--dtype", dtype, "--batch", str(B), "--streams", str(args.streams), "--steps", str(steps),
-                                "--warmup", "2", "--no-cpu-baseline", "--no-large-batch", "--no-f32-leg"] + flags, capture_output=True, text=True, timeout=900)
+                                "--warmup", "2", "--full", "--no-cpu-baseline", "--no-large-batch", "--no-f32-leg"] + flags, capture_output=True, text=True, timeout=900)
             return json.loads(r.stdout.strip().splitlines()[-1])
 
         def leg_roofline(rf, per_product):
